@@ -79,7 +79,41 @@ def parse_args():
                         "in-process remains the default")
     p.add_argument("--cp-workers", type=int, default=0,
                    help="control-plane worker processes (0 = auto)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step returned to its callers as DIR/<name>.npy "
+                        "(float32): `tokens` = generated token ids "
+                        "[calls, gen_len], and on the REST path `text_bytes` "
+                        "= UTF-8 bytes of each call's reply text, both "
+                        "padded with -1")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements and checks beyond the "
+                        "headline figure.  A plain run only sets up, warms "
+                        "up, times --steps steps and prints the result "
+                        "line; today the benchmark has nothing beyond that, "
+                        "so the flag changes nothing yet")
     return p.parse_args()
+
+
+# ------------------------------------------------------------ output dump
+def _padded(rows: list[list[int]], width: int = 0):
+    """Ragged int rows -> float32 [n, width] padded with -1 (token ids and
+    bytes are far below 2**24, so float32 holds them exactly)."""
+    import numpy as np
+    width = max([width] + [len(r) for r in rows])
+    a = np.full((len(rows), max(1, width)), -1.0, dtype=np.float32)
+    for i, r in enumerate(rows):
+        a[i, :len(r)] = r
+    return a
+
+
+def _dump_outputs(dirname: str, arrays: dict) -> None:
+    import numpy as np
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype == np.float32 and a.nbytes <= 32 << 20, name
+        np.save(out / f"{name}.npy", a)
 
 
 # --------------------------------------------------------------- REST mode
@@ -184,6 +218,17 @@ def run_rest(args, world: int, rank: int, dist, device: str, cfg) -> None:
                         device.startswith("cuda"),
                         dtype=kw.pop("dtype", dtype), seed=0, **kw)
         runner = EngineRunner(eng, ByteTokenizer(cfg.vocab_size))
+        if args.dump_outputs:
+            # keep every request's waiter: its "output" is the token list
+            # the engine hands back to app.ai() for that call
+            runner.waiters = []
+            _submit = runner.submit
+
+            def submit(*a, **k):
+                w = _submit(*a, **k)
+                runner.waiters.append(w)
+                return w
+            runner.submit = submit
         set_runner(args.model, runner)
 
     cp_proc = None
@@ -340,15 +385,31 @@ def _drive_and_report(args, world, device, cfg, dist, client, urls,
             "engine_proc": stats_url is not None,
         },
     }
+    if args.dump_outputs:
+        # the last timed step as its callers saw it.  Reply texts come back
+        # in call order; token rows are sorted, since the prompts are all
+        # the same and requests reach the engine in arrival order
+        client.stdin.write(json.dumps({"cmd": "last_texts"}) + "\n")
+        client.stdin.flush()
+        texts = json.loads(client.stdout.readline())["texts"]
+        arrays = {"text_bytes": _padded(
+            [list(t.encode("utf-8")) for t in texts])}
+        if runner is not None:
+            rows = [list(w["output"] or ())
+                    for w in runner.waiters[-args.calls:]]
+            arrays["tokens"] = _padded(sorted(rows), args.gen_len)
+        _dump_outputs(args.dump_outputs, arrays)
     print(json.dumps(out))
     client.stdin.close()
     if dist is not None:
         dist.barrier()  # teardown gate
 
 
-def run_step(eng: LLMEngine, rank: int, step: int, args) -> list[float]:
+def run_step(eng: LLMEngine, rank: int, step: int, args,
+             outputs: dict | None = None) -> list[float]:
     """Submit `calls` requests and drive the engine until all finish.
-    Returns per-call latencies (s)."""
+    Returns per-call latencies (s); `outputs`, if given, is filled with
+    each call's generated token ids, keyed by submission order."""
     g = torch.Generator().manual_seed(1000 * rank + step)
     sp = SamplingParams(max_tokens=args.gen_len, ignore_eos=True)
     t_submit = {}
@@ -359,13 +420,17 @@ def run_step(eng: LLMEngine, rank: int, step: int, args) -> list[float]:
         rid = eng.add_request(prompt, sp)
         assert rid is not None
         t_submit[rid] = time.perf_counter()
+    order = {rid: c for c, rid in enumerate(t_submit)}
     pending = set(t_submit)
     while pending:
         eng.step()
         for rid in list(pending):
-            if eng.get_finished(rid) is not None:
+            fin = eng.get_finished(rid)
+            if fin is not None:
                 lat.append(time.perf_counter() - t_submit[rid])
                 pending.discard(rid)
+                if outputs is not None:
+                    outputs[order[rid]] = list(fin.output_ids)
     return lat
 
 
@@ -376,6 +441,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     use_rest = (args.rest is None or args.rest) and args.tp <= 1
     dist = None
+    device = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
     if world > 1:
         import torch.distributed as dist_mod
         dist = dist_mod
@@ -385,11 +451,12 @@ def main():
             dist.init_process_group("gloo")
         else:
             dist.init_process_group(
-                "nccl" if torch.cuda.is_available() else "gloo")
-        if torch.cuda.is_available():
+                "nccl" if device.startswith("cuda") else "gloo")
+        if device.startswith("cuda"):
+            # --device cpu keeps every rank off the GPUs, however many
+            # (or few) the host has
             torch.cuda.set_device(local_rank)
 
-    device = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
     cfg = CONFIGS[args.model]
     if use_rest:
         if device == "cuda":
@@ -427,8 +494,9 @@ def main():
     barrier_sync()
     t0 = time.perf_counter()
     lats = []
+    outputs: dict = {}
     for s in range(args.steps):
-        lats.extend(run_step(eng, rank, s, args))
+        lats.extend(run_step(eng, rank, s, args, outputs))
     barrier_sync()
     elapsed = time.perf_counter() - t0
 
@@ -467,6 +535,10 @@ def main():
                 "tokens_per_sec": round(total_calls * (args.prompt_len + args.gen_len) / elapsed, 1),
             },
         }
+        if args.dump_outputs:
+            # each step overwrites the same keys: what is left is the last
+            _dump_outputs(args.dump_outputs, {"tokens": _padded(
+                [outputs[c] for c in sorted(outputs)], args.gen_len)})
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

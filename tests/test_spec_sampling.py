@@ -199,7 +199,10 @@ def test_spec_bench_tool():
     root = Path(__file__).resolve().parent.parent
     r = subprocess.run(
         [sys.executable, str(root / "tools" / "spec_bench.py"),
-         "--gen", "24", "--prompts", "4"],
+         "--gen", "24", "--prompts", "4",
+         # engine steps do not depend on the device; on the CPU the tool
+         # needs no share of a GPU that other tests may have filled
+         "--device", "cpu"],
         capture_output=True, text=True, timeout=300, cwd=root)
     assert r.returncode == 0, r.stderr[-1500:]
     out = _json.loads(r.stdout.strip().splitlines()[-1])

@@ -11,6 +11,8 @@ protocol on stdin/stdout:
 
 One input line = one benchmark step (submit N calls round-robin over
 targets and control-plane worker urls, wait for all).  EOF exits.
+{"cmd": "last_texts"} instead answers {"texts": [...]}: the reply text
+of each call of the previous step, in call order.
 The aiohttp session persists across steps, so keep-alive connections
 carry the whole run.
 """
@@ -31,6 +33,7 @@ async def run_step(session, spec) -> dict:
     sem = asyncio.Semaphore(spec.get("concurrency") or calls)
     lat: list[float] = []
     errors: dict[str, int] = {}
+    texts: list[str] = [""] * calls
 
     async def one(i: int):
         url = urls[i % len(urls)]
@@ -48,11 +51,15 @@ async def run_step(session, spec) -> dict:
                 status = f"error:{type(e).__name__}"
             if status == "completed":
                 lat.append((time.perf_counter() - t0) * 1e3)
+                res = body.get("result")
+                if isinstance(res, dict):
+                    texts[i] = str(res.get("text", ""))
             else:
                 errors[status] = errors.get(status, 0) + 1
 
     await asyncio.gather(*(one(i) for i in range(calls)))
-    return {"ok": len(lat), "errors": errors, "latencies_ms": lat}
+    return {"ok": len(lat), "errors": errors, "latencies_ms": lat,
+            "texts": texts}
 
 
 async def main():
@@ -64,13 +71,18 @@ async def main():
     reader = asyncio.StreamReader()
     await loop.connect_read_pipe(
         lambda: asyncio.StreamReaderProtocol(reader), sys.stdin)
+    last_texts: list[str] = []
     try:
         while True:
             line = await reader.readline()
             if not line:
                 break
             spec = json.loads(line)
-            out = await run_step(session, spec)
+            if spec.get("cmd") == "last_texts":
+                out = {"texts": last_texts}
+            else:
+                out = await run_step(session, spec)
+                last_texts = out.pop("texts")
             sys.stdout.write(json.dumps(out) + "\n")
             sys.stdout.flush()
     finally:

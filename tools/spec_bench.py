@@ -64,8 +64,11 @@ def main():
     ap.add_argument("--gen", type=int, default=48)
     ap.add_argument("--prompts", type=int, default=8)
     ap.add_argument("--k", type=int, default=4)
+    ap.add_argument("--device", default=None,
+                    help="default: cuda when a GPU is visible, else cpu")
     args = ap.parse_args()
-    device = "cuda" if torch.cuda.is_available() else "cpu"
+    device = args.device or (
+        "cuda" if torch.cuda.is_available() else "cpu")
     rng = random.Random(5)
     V = CONFIGS[args.model].vocab_size
     prompts = []
