@@ -139,7 +139,9 @@ class LLMEngine:
         self._graphs: dict[int, dict] = {}
         self.metrics = {"prefill_tokens": 0, "decode_tokens": 0, "steps": 0,
                         "prefill_steps": 0, "decode_steps": 0,
-                        "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0}
+                        "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0,
+                        # each _step_decode is one or the other
+                        "decode_graph_steps": 0, "decode_eager_steps": 0}
         # prompt-lookup speculative decoding (greedy-exact, opt-in):
         # draft-model speculation (greedy-exact): a small model proposes
         # spec_draft_k tokens per step; the main model verifies them in
@@ -173,6 +175,8 @@ class LLMEngine:
         # static decode buffers (shared across graph buckets; sized to max)
         B = max_num_seqs
         dev = self.device
+        self._mask_words = (cfg.vocab_size + 31) // 32
+        self._byte_bits: dict[tuple, torch.Tensor] = {}  # see _json_allowed
         self._dec = {
             "ids": torch.zeros(B, dtype=torch.int32, device=dev),
             "pos": torch.zeros(B, dtype=torch.int32, device=dev),
@@ -187,6 +191,10 @@ class LLMEngine:
             "lp_tok": torch.zeros(B, dtype=torch.float32, device=dev),
             "lp_vals": torch.zeros(B, LP_TOPN, dtype=torch.float32, device=dev),
             "lp_ids": torch.zeros(B, LP_TOPN, dtype=torch.int32, device=dev),
+            # packed grammar token mask, bit v&31 of word v>>5 (written
+            # only on steps with a json_mode row; read by jm-keyed graphs)
+            "allow": torch.full((B, self._mask_words), -1,
+                                dtype=torch.int32, device=dev),
         }
         self._host = {k: torch.zeros_like(v, device="cpu").pin_memory()
                       if self.is_gpu else torch.zeros_like(v)
@@ -376,17 +384,23 @@ class LLMEngine:
             return [], []
         last_rows = torch.tensor(done_rows, dtype=torch.int32, device=dev)
         logits = self.model(ids_t, pos_t, self.kv, md, logit_rows=last_rows)
-        if any(s.sampling.json_mode for s in done):
-            logits = logits + self._json_mask(done).to(logits.dtype)
         temps = torch.tensor([s.sampling.temperature for s in done],
                              dtype=torch.float32, device=dev)
         kw = {}
+        if any(s.sampling.json_mode for s in done):
+            allow = torch.empty(len(done), self._mask_words,
+                                dtype=torch.int32)
+            self._fill_allow_rows(allow, done)
+            kw["allowed"] = allow.to(dev)
+            if any(s.sampling.logprobs > 0 for s in done):
+                ops.mask_logits_(logits, kw["allowed"])
         if any(s.sampling.top_k > 0 or s.sampling.top_p < 1.0 for s in done) \
                 and dev.type == "cuda":
-            kw = {"topk": torch.tensor([s.sampling.top_k for s in done],
-                                       dtype=torch.int32, device=dev),
-                  "topp": torch.tensor([s.sampling.top_p for s in done],
-                                       dtype=torch.float32, device=dev)}
+            kw.update(
+                topk=torch.tensor([s.sampling.top_k for s in done],
+                                  dtype=torch.int32, device=dev),
+                topp=torch.tensor([s.sampling.top_p for s in done],
+                                  dtype=torch.float32, device=dev))
         toks = ops.sample(logits, temps, self.sampler, **kw)
         if any(s.sampling.logprobs > 0 for s in done):
             self._attach_row_logprobs(done, logits, toks)
@@ -419,10 +433,12 @@ class LLMEngine:
     def set_token_grammar(self, grammar) -> None:
         self.token_grammar = grammar
 
-    def _json_allowed(self, seq: Sequence) -> list[int]:
-        """Token ids legal for seq's next token under the JSON grammar,
+    def _json_allowed(self, seq: Sequence) -> torch.Tensor:
+        """Packed mask (int32 [W], ops.pack_token_mask format) of the
+        tokens legal for seq's next token under the JSON grammar and
         completable within its remaining budget.  The FSM is cached on the
-        sequence and rebuilt after preemption (output_ids reset)."""
+        sequence and rebuilt after preemption (output_ids reset).  The
+        result may be a shared cache entry: copy it, never write to it."""
         from .jsonfsm import EOS_ID, JsonFSM
         grammar = getattr(self, "token_grammar", None)
         fsm = getattr(seq, "_fsm", None)
@@ -457,26 +473,39 @@ class LLMEngine:
                 "seq %d: grammar-invalid token in history; disabling "
                 "json_mode for it", seq.seq_id)
             seq.sampling.json_mode = False
-            return list(range(self.cfg.vocab_size))
+            return torch.full((self._mask_words,), -1, dtype=torch.int32)
         seq._fsm, seq._fsm_pos = fsm, len(seq.output_ids)
         remaining = seq.sampling.max_tokens - len(seq.output_ids)
-        if grammar is not None:
-            return grammar.allowed_token_ids(fsm, remaining)
-        ids = fsm.allowed_token_ids(remaining)
-        return [self.eos_id if i == EOS_ID else i for i in ids]
-
-    def _json_mask(self, seqs: list[Sequence]) -> torch.Tensor:
-        """Additive [len(seqs), V] mask: 0 for allowed, -inf elsewhere for
-        json_mode rows; all-0 for unconstrained rows."""
         V = self.cfg.vocab_size
-        mask = torch.zeros(len(seqs), V)
+        if grammar is not None:
+            return grammar.allowed_token_bits(fsm, remaining, V)
+        key = None
+        if type(fsm) is JsonFSM:
+            # the byte PDA's mask is a function of its signature (the
+            # budget stops binding past stack depth + 12), so rows repeat
+            # across steps and sequences: pay the PDA walk once per state
+            from .token_grammar import TokenJsonGrammar
+            key = TokenJsonGrammar._sig(fsm, remaining)
+            hit = self._byte_bits.get(key)
+            if hit is not None:
+                return hit
+        ids = fsm.allowed_token_ids(remaining)
+        bits = ops.pack_token_mask(
+            [self.eos_id if i == EOS_ID else i for i in ids], V)
+        if key is not None:
+            self._byte_bits[key] = bits
+        return bits
+
+    def _fill_allow_rows(self, rows: torch.Tensor,
+                         seqs: list[Sequence]) -> None:
+        """Write the packed token mask of a step into host rows [>=n, W]:
+        the grammar's mask for json_mode rows, all ones for unconstrained
+        rows and padding lanes.  No dense [n, V] mask exists anywhere; the
+        sampler kernels read the bits (csrc/sampling.hip)."""
+        rows.fill_(-1)
         for i, seq in enumerate(seqs):
             if seq.sampling.json_mode:
-                # -1e30 not -inf: stays finite through the bf16 top-k/p
-                # histogram sampler while still contributing zero mass
-                mask[i] = -1e30
-                mask[i, self._json_allowed(seq)] = 0.0
-        return mask.to(self.device)
+                rows[i].copy_(self._json_allowed(seq))
 
     # -- speculative decode: draft model (greedy-exact) ---------------------
     def _spec_cap(self, seq: Sequence, k: int) -> int:
@@ -739,7 +768,8 @@ class LLMEngine:
         return events
 
     # -- decode path (graph-captured on GPU) --------------------------------
-    def _fill_decode_buffers(self, seqs: list[Sequence], bs: int) -> None:
+    def _fill_decode_buffers(self, seqs: list[Sequence], bs: int,
+                             jm: bool = False) -> None:
         h = self._host
         for i, seq in enumerate(seqs):
             n = seq.num_tokens
@@ -766,17 +796,22 @@ class LLMEngine:
         for k in ("ids", "pos", "slots", "lens", "temps", "topk", "topp"):
             d[k][:bs].copy_(h[k][:bs], non_blocking=nb)
         d["bt"][:bs].copy_(h["bt"][:bs], non_blocking=nb)
+        if jm:  # steps without a constrained row copy nothing
+            self._fill_allow_rows(h["allow"][:bs], seqs)
+            d["allow"][:bs].copy_(h["allow"][:bs], non_blocking=nb)
 
     def _decode_forward(self, bs: int, nsplit: int, scratch, tkp: bool,
-                        lp: bool = False, mask: torch.Tensor | None = None):
+                        lp: bool = False, jm: bool = False):
         d = self._dec
         md = AttnMetadata(is_prefill=False, slots=d["slots"][:bs],
                           block_table=d["bt"][:bs], seq_lens_t=d["lens"][:bs],
                           nsplit=nsplit, decode_scratch=scratch)
         logits = self.model(d["ids"][:bs], d["pos"][:bs], self.kv, md)
-        if mask is not None:  # grammar-constrained rows (eager only)
-            logits = logits + mask.to(logits.dtype)
         kw = {"topk": d["topk"][:bs], "topp": d["topp"][:bs]} if tkp else {}
+        if jm:  # grammar-constrained rows: the sampler reads the bitmask
+            kw["allowed"] = d["allow"][:bs]
+            if lp:  # logprobs are reported over the legal tokens only
+                ops.mask_logits_(logits, kw["allowed"])
         ops.sample(logits, d["temps"][:bs], self.sampler,
                    out=d["tokens"][:bs], **kw)
         if lp:  # graph-capturable logprob reporting
@@ -799,8 +834,9 @@ class LLMEngine:
                           dtype=torch.float32, device=self.device)
         return po, pml
 
-    def _get_graph(self, bs: int, tkp: bool, lp: bool = False):
-        key = (bs, tkp, lp)
+    def _get_graph(self, bs: int, tkp: bool, lp: bool = False,
+                   jm: bool = False):
+        key = (bs, tkp, lp, jm)
         entry = self._graphs.get(key)
         if entry is not None:
             return entry
@@ -811,11 +847,11 @@ class LLMEngine:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):
-                self._decode_forward(bs, nsplit, scratch, tkp, lp)
+                self._decode_forward(bs, nsplit, scratch, tkp, lp, jm)
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._decode_forward(bs, nsplit, scratch, tkp, lp)
+            self._decode_forward(bs, nsplit, scratch, tkp, lp, jm)
         entry = {"graph": g, "nsplit": nsplit, "scratch": scratch}
         self._graphs[key] = entry
         return entry
@@ -849,19 +885,17 @@ class LLMEngine:
         tkp = any(s.sampling.top_k > 0 or s.sampling.top_p < 1.0 for s in seqs)
         lp = any(s.sampling.logprobs > 0 for s in seqs)
         jm = any(s.sampling.json_mode for s in seqs)
-        self._fill_decode_buffers(seqs, bs)
-        if self.enable_graphs and not jm:
-            self._get_graph(bs, tkp, lp)["graph"].replay()
+        # only the CONTENTS of a grammar mask depend on the data: the packed
+        # bits sit in a static buffer, so jm steps replay a graph as well
+        self._fill_decode_buffers(seqs, bs, jm)
+        if self.enable_graphs:
+            self.metrics["decode_graph_steps"] += 1
+            self._get_graph(bs, tkp, lp, jm)["graph"].replay()
         else:
-            # json grammar masks are data-dependent -> eager decode
-            mask = None
-            if jm:
-                mask = torch.zeros(bs, self.cfg.vocab_size,
-                                   device=self.device)
-                mask[:n] = self._json_mask(seqs)
+            self.metrics["decode_eager_steps"] += 1
             nsplit = choose_nsplit(bs, self.cfg.num_kv_heads) if self.is_gpu else 1
             self._decode_forward(bs, nsplit, self._make_scratch(bs, nsplit),
-                                 tkp, lp, mask)
+                                 tkp, lp, jm)
         if lp:
             self._attach_decode_logprobs(seqs, n)
         toks = self._dec["tokens"][:n]

@@ -63,6 +63,7 @@ class TokenJsonGrammar:
                 "vocabulary lacks single-byte fallback tokens for "
                 f"{missing}; the budget guarantee would not hold")
         self._mask_cache: dict[tuple, list[int]] = {}
+        self._bits_cache: dict[tuple, "object"] = {}
 
     # ------------------------------------------------------------- engine API
     def advance_token(self, fsm: JsonFSM, tid: int) -> None:
@@ -112,6 +113,25 @@ class TokenJsonGrammar:
                     stack.append((child, f2))
         self._mask_cache[sig] = out
         return out
+
+    def allowed_token_bits(self, fsm, remaining: int, V: int | None = None):
+        """allowed_token_ids as the sampler's packed bitmask (int32 [W],
+        ops.pack_token_mask format) over a logits width V (default: the
+        vocabulary table's length; models pad their LM head past it).
+        Memoized by the same signature as allowed_token_ids, so a hit
+        costs the caller one row copy.  The returned tensor is shared:
+        copy it, never write to it."""
+        from ..ops import pack_token_mask
+        if V is None:
+            V = len(self.vocab)
+        if hasattr(fsm, "sig"):
+            remaining = min(remaining, self.SCHEMA_BUDGET_CAP)
+        key = (self._sig(fsm, remaining), V)
+        hit = self._bits_cache.get(key)
+        if hit is None:
+            hit = self._bits_cache[key] = pack_token_mask(
+                self.allowed_token_ids(fsm, remaining), V)
+        return hit
 
 
 def vocab_bytes_from_hf(tok, vocab_size: int) -> list[bytes | None]:

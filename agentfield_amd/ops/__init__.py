@@ -384,27 +384,86 @@ class SamplerState:
         self.hist_m = torch.empty(max_b, 256, dtype=torch.float32, device=device)
 
 
+def pack_token_mask(ids_or_bool, V: int) -> torch.Tensor:
+    """Pack a set of legal tokens into the sampler's bitmask: int32 [W],
+    W = (V+31)//32, token v legal iff bit (v & 31) (LSB first) of word
+    v >> 5 is set; bits at positions >= V are 0.  Takes token ids (list,
+    array or integer tensor) or a bool [V] membership vector."""
+    return ref.pack_token_mask(ids_or_bool, V)
+
+
+def unpack_token_mask(bits: torch.Tensor, V: int) -> torch.Tensor:
+    """Inverse of pack_token_mask: int32 [..., W] -> bool [..., V] (CPU)."""
+    return ref.unpack_token_mask(bits, V)
+
+
+def _check_allowed(allowed: torch.Tensor, B: int, V: int) -> None:
+    if (allowed.dtype != torch.int32 or not allowed.is_contiguous()
+            or tuple(allowed.shape) != (B, (V + 31) // 32)):
+        raise ValueError(
+            f"allowed must be contiguous int32 [{B}, {(V + 31) // 32}], got "
+            f"{allowed.dtype} {tuple(allowed.shape)}")
+
+
+def mask_logits_(logits: torch.Tensor, allowed: torch.Tensor) -> torch.Tensor:
+    """In place: -inf over the entries of logits [B,V] whose bit in the
+    packed mask allowed [B,W] is clear; allowed entries keep their bits.
+    Only for paths that need masked LOGITS (logprob reporting) — a masked
+    draw passes `allowed` to sample() instead."""
+    B, V = logits.shape
+    _check_allowed(allowed, B, V)
+    if not _on_gpu(logits):
+        return ref.mask_logits_(logits, allowed)
+    if logits.dtype != torch.bfloat16 or logits.stride(1) != 1 \
+            or not allowed.is_cuda:
+        raise ValueError("mask_logits_ needs bf16 logits with unit column "
+                         "stride and a device mask")
+    rc = _lib.lib().af_mask_logits(_lib.ptr(logits), _lib.ptr(allowed), B, V,
+                                   logits.stride(0) if B > 1 else V,
+                                   _lib.cur_stream())
+    _lib.check(rc, "af_mask_logits")
+    return logits
+
+
 def sample(logits: torch.Tensor, temps: torch.Tensor, state: SamplerState,
            out: torch.Tensor | None = None,
            topk: torch.Tensor | None = None,
-           topp: torch.Tensor | None = None) -> torch.Tensor:
+           topp: torch.Tensor | None = None,
+           allowed: torch.Tensor | None = None) -> torch.Tensor:
     """Greedy (temp==0) or Gumbel-max temperature sampling; optional
     top-k/top-p nucleus restriction (sort-free histogram threshold).
-    logits [B,V] bf16; topk [B] i32 (0 = off); topp [B] f32 (>=1 = off)."""
+    logits [B,V] bf16; topk [B] i32 (0 = off); topp [B] f32 (>=1 = off).
+    allowed [B,W] i32 (pack_token_mask format) restricts each row to its
+    set bits: a disallowed token is never looked at; a row with no bit set
+    yields token 0."""
     B, V = logits.shape
+    if allowed is not None:
+        _check_allowed(allowed, B, V)
     if not _on_gpu(logits):
-        res = ref.sample_greedy(logits)
+        res = ref.sample_greedy(logits, allowed)
         if out is not None:
             out[:B].copy_(res)
             return out
         return res
     if out is None:
         out = torch.empty(B, dtype=torch.int32, device=logits.device)
+    if allowed is not None and not allowed.is_cuda:
+        raise ValueError("allowed must live on the logits' device")
     if topk is not None or topp is not None:
         if topk is None:
             topk = torch.zeros(B, dtype=torch.int32, device=logits.device)
         if topp is None:
             topp = torch.ones(B, dtype=torch.float32, device=logits.device)
+        if allowed is not None:
+            rc = _lib.lib().af_sample_topkp_masked(
+                _lib.ptr(out), _lib.ptr(state.pv), _lib.ptr(state.pi),
+                _lib.ptr(state.rmax), _lib.ptr(state.thresh),
+                _lib.ptr(state.hist_n), _lib.ptr(state.hist_m),
+                _lib.ptr(logits), _lib.ptr(temps), _lib.ptr(topk),
+                _lib.ptr(topp), _lib.ptr(state.step), state.seed, B, V,
+                _lib.ptr(allowed), _lib.cur_stream())
+            _lib.check(rc, "af_sample_topkp_masked")
+            return out
         rc = _lib.lib().af_sample_topkp(
             _lib.ptr(out), _lib.ptr(state.pv), _lib.ptr(state.pi),
             _lib.ptr(state.rmax), _lib.ptr(state.thresh),
@@ -412,6 +471,13 @@ def sample(logits: torch.Tensor, temps: torch.Tensor, state: SamplerState,
             _lib.ptr(temps), _lib.ptr(topk), _lib.ptr(topp),
             _lib.ptr(state.step), state.seed, B, V, _lib.cur_stream())
         _lib.check(rc, "af_sample_topkp")
+        return out
+    if allowed is not None:
+        rc = _lib.lib().af_sample_masked(
+            _lib.ptr(out), _lib.ptr(state.pv), _lib.ptr(state.pi),
+            _lib.ptr(logits), _lib.ptr(temps), _lib.ptr(state.step),
+            state.seed, B, V, _lib.ptr(allowed), _lib.cur_stream())
+        _lib.check(rc, "af_sample_masked")
         return out
     rc = _lib.lib().af_sample(
         _lib.ptr(out), _lib.ptr(state.pv), _lib.ptr(state.pi), _lib.ptr(logits),

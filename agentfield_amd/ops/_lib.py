@@ -66,6 +66,10 @@ def _declare(l: ctypes.CDLL) -> None:
     l.af_sample.argtypes = [p, p, p, p, p, p, u32, i, i, p]
     l.af_sample_topkp.argtypes = [p, p, p, p, p, p, p, p, p, p, p, p,
                                   u32, i, i, p]
+    l.af_sample_masked.argtypes = [p, p, p, p, p, p, u32, i, i, p, p]
+    l.af_sample_topkp_masked.argtypes = [p, p, p, p, p, p, p, p, p, p, p, p,
+                                         u32, i, i, p, p]
+    l.af_mask_logits.argtypes = [p, p, i, i, i64, p]
     l.af_gather_rows.argtypes = [p, p, p, i, i, p]
     l.af_mfma_probe.argtypes = [p, p, p, p]
     l.af_mfma_mx_probe.argtypes = [p, p, p, p, p, p]
@@ -77,7 +81,8 @@ def _declare(l: ctypes.CDLL) -> None:
                "af_reshape_and_cache", "af_embedding", "af_attn_decode",
                "af_attn_prefill", "af_gemm_bf16", "af_gemm_bf16_ring", "af_gemm_bf16_q8", "af_gemm_mxfp8", "af_oneshot_allreduce",
                "af_gemm_skinny", "af_sample",
-               "af_sample_topkp", "af_gather_rows", "af_mfma_probe", "af_mfma_mx_probe", "af_lds_stride_probe", "af_mfma_mx32_probe", "af_axpy",
+               "af_sample_topkp", "af_sample_masked",
+               "af_sample_topkp_masked", "af_mask_logits", "af_gather_rows", "af_mfma_probe", "af_mfma_mx_probe", "af_lds_stride_probe", "af_mfma_mx32_probe", "af_axpy",
                "af_device_sync"):
         getattr(l, fn).restype = ctypes.c_int
 

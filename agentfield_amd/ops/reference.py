@@ -129,5 +129,53 @@ def attn_prefill_paged(q, kcache, vcache, block_table, q_start, cu_seqlens,
     return out
 
 
-def sample_greedy(logits):
-    return logits.float().argmax(-1).int()
+def sample_greedy(logits, allowed=None):
+    lf = logits.float()
+    if allowed is not None:
+        keep = unpack_token_mask(allowed, logits.shape[-1]).to(lf.device)
+        lf = lf.masked_fill(~keep, float("-inf"))
+    return lf.argmax(-1).int()
+
+
+def pack_token_mask(ids_or_bool, V):
+    """Token ids or bool [V] -> int32 [W] bitmask, W = (V+31)//32, bit
+    v & 31 (LSB first) of word v >> 5; bits >= V are 0."""
+    import numpy as np
+    W = (V + 31) // 32
+    if isinstance(ids_or_bool, torch.Tensor):
+        ids_or_bool = ids_or_bool.detach().cpu().numpy()
+    a = np.asarray(ids_or_bool)
+    member = np.zeros(W * 32, dtype=np.bool_)
+    if a.dtype == np.bool_:
+        if a.shape != (V,):
+            raise ValueError(f"bool mask must have shape ({V},)")
+        member[:V] = a
+    else:
+        idx = a.astype(np.int64).ravel()
+        if idx.size and (idx.min() < 0 or idx.max() >= V):
+            raise ValueError(f"token id outside [0, {V})")
+        if idx.size * 16 < V:  # sparse set: skip the O(V) pass
+            words = np.zeros(W, dtype=np.uint32)
+            np.bitwise_or.at(words, idx >> 5,
+                             np.left_shift(1, idx & 31).astype(np.uint32))
+            return torch.from_numpy(words.view(np.int32))
+        member[idx] = True
+    words = np.packbits(member, bitorder="little").view("<i4")
+    return torch.from_numpy(words.astype(np.int32, copy=False))
+
+
+def unpack_token_mask(bits, V):
+    """int32 [..., W] bitmask -> bool [..., V] (CPU)."""
+    import numpy as np
+    a = bits.detach().cpu().contiguous().numpy()
+    if a.dtype != np.int32 or a.shape[-1] != (V + 31) // 32:
+        raise ValueError(f"mask must be int32 [..., {(V + 31) // 32}] for "
+                         f"V={V}, got {a.dtype} {a.shape}")
+    by = a.view(np.uint8)
+    return torch.from_numpy(
+        np.unpackbits(by, axis=-1, bitorder="little")[..., :V].astype(np.bool_))
+
+
+def mask_logits_(logits, allowed):
+    keep = unpack_token_mask(allowed, logits.shape[-1]).to(logits.device)
+    return logits.masked_fill_(~keep, float("-inf"))
