@@ -34,16 +34,21 @@ HIP_SOURCES = [
     "gemm_mxfp8.hip",
     "allreduce.hip",
     "gemm_skinny.hip",
+    "gemm_skinny_w8.hip",
     "sampling.hip",
     "probe.hip",
 ]
+
+
+def _headers() -> list[Path]:
+    return sorted(CSRC.glob("*.h"))
 
 
 def _needs_build() -> bool:
     if not LIB.exists():
         return True
     lib_m = LIB.stat().st_mtime
-    deps = [CSRC / s for s in HIP_SOURCES] + [CSRC / "common.h", Path(__file__)]
+    deps = [CSRC / s for s in HIP_SOURCES] + _headers() + [Path(__file__)]
     return any(d.stat().st_mtime > lib_m for d in deps)
 
 
@@ -54,13 +59,14 @@ def build_afops(force: bool = False, verbose: bool = True) -> Path:
     objdir = CSRC / ".obj"
     objdir.mkdir(exist_ok=True)
     objs = []
+    hdr_m = max(h.stat().st_mtime for h in _headers())
     for src in HIP_SOURCES:
         sp = CSRC / src
         op = objdir / (src + ".o")
         objs.append(op)
         if (not force and op.exists()
                 and op.stat().st_mtime > sp.stat().st_mtime
-                and op.stat().st_mtime > (CSRC / "common.h").stat().st_mtime):
+                and op.stat().st_mtime > hdr_m):
             continue
         cmd = [
             HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",

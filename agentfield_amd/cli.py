@@ -129,7 +129,7 @@ def engine(model: list[str] = ["llama-3-8b"], device: str = None,
            host: str = "127.0.0.1", port: int = 8710,
            max_num_seqs: int = 256, max_prefill_tokens: int = 0,
            spec_lookup: int = 0, no_graphs: bool = False,
-           prefix_cache: bool = False):
+           prefix_cache: bool = False, quant: str = None):
     """Run one GPU engine server (start one per GPU for DP; repeat
     --model to co-serve several models from one replica)."""
     from .serving.engine_server import main as engine_main
@@ -144,6 +144,8 @@ def engine(model: list[str] = ["llama-3-8b"], device: str = None,
         argv += ["--model", m]
     if prefix_cache:
         argv.append("--prefix-cache")
+    if quant:
+        argv += ["--quant", quant]
     if device:
         argv += ["--device", device]
     sys.argv = ["engine_server"] + argv

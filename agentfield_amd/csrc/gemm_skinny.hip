@@ -14,40 +14,7 @@
 //     (out = silu(gate)*up) for the gate_up projection, or residual-add
 //   * hipBLASLt's MT16 kernels run at ~1.7-2.6 TB/s on the N=4096/6144
 //     decode shapes; this path targets the ~6 TB/s achievable ceiling
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8s;
-
-__device__ __forceinline__ bf16x8s as_bf16x8s(s16x8 v) {
-  union { s16x8 s; bf16x8s b; } u;
-  u.s = v;
-  return u.b;
-}
-
-// Stage a 64x64 bf16 tile (8 KiB) into linear LDS with read-side swizzle
-// pre-applied to the global source.  2 x 16 B per thread.
-__device__ __forceinline__ void stage64(const u16* __restrict__ g, size_t ld,
-                                        u16* lds, int row0, int k0,
-                                        int max_row) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int e = (it * 256 + tid) * 8;
-    const int row = e >> 6;
-    const int wb = (e & 63) * 2;
-    const int wsw = wb ^ ((row & 7) << 4);
-    const u16* src = g + (size_t)min(row0 + row, max_row - 1) * ld + k0 + (wsw >> 1);
-    u16* dst = lds + (size_t)(it * 256 + (tid & ~63)) * 8;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) uint32_t*)src,
-        (__attribute__((address_space(3))) uint32_t*)dst, 16, 0, 0);
-  }
-}
-
-__device__ __forceinline__ s16x8 frag64(const u16* lds, int row, int byte) {
-  return *reinterpret_cast<const s16x8*>(
-      reinterpret_cast<const char*>(lds) + row * 128 + (byte ^ ((row & 7) << 4)));
-}
+#include "gemm_skinny.h"  // stage64 / frag64, K split, combine launches
 
 // MT = number of 16-row M tiles (ceil(M/16)); grid (N/64, SK), block 256.
 template <int MT>
@@ -222,8 +189,7 @@ AF_EXPORT int af_gemm_skinny(void* out, void* partial, void* residual,
   if (M < 1 || M > 256) return 9005;
   if (N % 64 || K % 64) return 9006;
   hipStream_t st = (hipStream_t)stream;
-  int Kc = ((K / SK + 63) / 64) * 64;
-  while ((SK - 1) * Kc >= K) --SK;  // drop empty splits
+  const int Kc = af_skinny_split(K, &SK);
   dim3 grid(N / 64, SK), blk(256);
   const int MT = (M + 15) / 16;
 #define AF_SK_LAUNCH(MTV)                                                      \
@@ -248,20 +214,6 @@ AF_EXPORT int af_gemm_skinny(void* out, void* partial, void* residual,
     default: AF_SK_LAUNCH(16); break;
   }
 #undef AF_SK_LAUNCH
-  if (mode == 4) {
-    if (N % 32) return 9007;
-    dim3 g4(M, 8);
-    gemm_skinny_combine_row_kernel<<<g4, 256, 0, st>>>(
-        (u16*)out, (u16*)residual, (const float*)partial, (float*)ss_out,
-        M, N, SK);
-    return af_last_err();
-  }
-  const int cols = (mode == 2) ? N / 2 : N;
-  i64 total = (i64)M * (cols / 4);
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 1024) blocks = 1024;
-  gemm_skinny_combine_kernel<<<blocks, 256, 0, st>>>(
-      (u16*)out, (u16*)residual, (const float*)partial, M, N, SK, mode,
-      (const float*)scale_ss, 1.f / (float)K, eps);
-  return af_last_err();
+  return af_skinny_combine(out, partial, residual, M, N, K, SK, mode,
+                           scale_ss, eps, ss_out, st);
 }

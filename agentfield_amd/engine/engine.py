@@ -47,7 +47,7 @@ class LLMEngine:
                  tp_group=None, spec_lookup: int = 0,
                  spec_draft=None, spec_draft_k: int = 4,
                  draft_model: "LlamaForCausalLM | None" = None,
-                 prefix_cache: bool = False):
+                 prefix_cache: bool = False, quant: str | None = None):
         self.cfg = cfg
         self.device = torch.device(device)
         self.is_gpu = self.device.type == "cuda"
@@ -58,6 +58,17 @@ class LLMEngine:
         if self.device.type == "cuda" and tp_group is None and \
                 not getattr(model, "no_fused_decode", False):
             self.model.fold_norm_weights()
+        # weight quantization (opt-in) — after the fold, which rewrites qkv
+        # and gate_up, and before the KV budget is read from free memory so
+        # the fp8 copies are accounted for.  On CPU the weights are only
+        # fake-quantized (the oracle for the fp8 decode path).  A draft
+        # model stays bf16.
+        self.quant = quant
+        if quant is not None:
+            if tp_group is not None:
+                raise ValueError("quant with tensor/expert parallelism is "
+                                 "not supported yet")
+            self.model.quantize_weights(quant)
 
         if num_pages is None:
             if self.is_gpu:

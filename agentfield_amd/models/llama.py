@@ -296,17 +296,31 @@ class LlamaLayer(nn.Module):
         return h, residual
 
     def forward_decode_fused(self, residual, ss, ss2, positions, rope_tab,
-                             kv, md):
+                             kv, md, w8: bool = False, w8_min_elems: int = 0):
         """Decode fast path: RMSNorms fold into the skinny GEMMs — input
         normalization happens in the GEMM's X staging (from per-row
         sum-of-squares stats), residual-add + next-norm stats in the GEMM
-        combine.  Zero standalone norm kernels per layer."""
+        combine.  Zero standalone norm kernels per layer.
+
+        w8: stream the skinny GEMMs' weights from the MX-fp8 buffers that
+        quantize_weights registered (same matrix, half the bytes, same
+        bits out).  At M <= 64 a matrix of fewer than w8_min_elems elements
+        keeps its bf16 stream: there the fp8 stream measured no faster
+        (docs/QUANTIZATION.md)."""
         at, mlp = self.attn, self.mlp
+        M = residual.shape[0]
+
+        def wq(mod, name):
+            if not w8 or (M <= 64
+                          and getattr(mod, name).numel() < w8_min_elems):
+                return None
+            return getattr(mod, name + "_q8"), getattr(mod, name + "_s8")
         M = residual.shape[0]
         K = residual.shape[1]
         small = M <= 64  # measured crossover vs hipBLASLt (BENCHMARKS.md)
         if small:
-            qkv = ops.linear_skinny(residual, at.qkv, scale=(ss, self.eps))
+            qkv = ops.linear_skinny(residual, at.qkv, scale=(ss, self.eps),
+                                    wq=wq(at, "qkv"))
             o = at.attend(qkv, positions, rope_tab, kv, md)
         else:
             # blas GEMM on the un-normalized rows; the RMSNorm scalar rides
@@ -314,19 +328,30 @@ class LlamaLayer(nn.Module):
             qkv = residual @ at.qkv.t()
             o = at.attend(qkv, positions, rope_tab, kv, md,
                           scale=(ss, K, self.eps))
-        ops.linear_skinny(o, at.o, mode=4, residual=residual, ss_out=ss2)
+        ops.linear_skinny(o, at.o, mode=4, residual=residual, ss_out=ss2,
+                          wq=wq(at, "o"))
         if small:
             act = ops.linear_skinny(residual, mlp.gate_up, mode=2,
-                                    scale=(ss2, self.eps))
+                                    scale=(ss2, self.eps),
+                                    wq=wq(mlp, "gate_up"))
         else:
             act = ops.silu_and_mul(residual @ mlp.gate_up.t(),
                                    scale=(ss2, K, self.eps))
-        ops.linear_skinny(act, mlp.down, mode=4, residual=residual, ss_out=ss)
+        ops.linear_skinny(act, mlp.down, mode=4, residual=residual, ss_out=ss,
+                          wq=wq(mlp, "down"))
         return residual, ss
 
 
 class LlamaForCausalLM(nn.Module):
     """The model proper.  TP-sharded variants are built by parallel.tp."""
+
+    # quant="mxfp8" decode dispatch: at M <= 64 only matrices of at least
+    # this many elements stream as fp8.  Measured on MI355X (llama-3-8b
+    # shapes, docs/QUANTIZATION.md): down (58.7M) and gate_up (117M) are
+    # faster as fp8, qkv (25.2M) and o (16.8M) are not — their launches are
+    # dominated by fixed costs, not bytes.  0 sends every projection through
+    # the fp8 kernel.
+    w8_min_elems = 1 << 25
 
     def __init__(self, cfg: LlamaConfig, device="cpu", dtype=torch.bfloat16):
         super().__init__()
@@ -385,6 +410,46 @@ class LlamaForCausalLM(nn.Module):
         self._norms_folded = True
         return self
 
+    @torch.no_grad()
+    def quantize_weights(self, fmt: str = "mxfp8"):
+        """Put every dense layer's qkv / o / gate_up / down on the MX-fp8
+        grid (OCP e4m3 + one E8M0 scale per 32-element K-block).
+
+        The bf16 parameter is overwritten with the dequantized values —
+        exactly representable, so every path that reads the parameter
+        (prefill, eager, CPU, speculative verify) computes with the same
+        numbers as the fused decode path, which streams the fp8 bytes from
+        the non-persistent buffers <name>_q8 / <name>_s8 and rebuilds the
+        same bf16 values in registers.  Both encodings stay resident
+        (about 1.53x the bf16 bytes of these matrices).  embed, lm_head,
+        norms and the router are left alone.  Run after fold_norm_weights:
+        folding rewrites qkv and gate_up."""
+        from ..quant import dequantize_mx, quantize_mx
+        if fmt != "mxfp8":
+            raise ValueError(f"unknown quantization format {fmt!r} "
+                             "(supported: 'mxfp8')")
+        if self.cfg.num_experts > 1:
+            raise ValueError("quantize_weights: MoE expert weights are not "
+                             "supported yet")
+        if getattr(self, "quant", None) == fmt:
+            return self
+        for layer in self.layers:
+            for mod, name in ((layer.attn, "qkv"), (layer.attn, "o"),
+                              (layer.mlp, "gate_up"), (layer.mlp, "down")):
+                w = getattr(mod, name)
+                q8, s8 = quantize_mx(w)
+                w.copy_(dequantize_mx(q8, s8).to(w.dtype))
+                mod.register_buffer(name + "_q8", q8.contiguous(),
+                                    persistent=False)
+                mod.register_buffer(name + "_s8", s8.contiguous(),
+                                    persistent=False)
+        self.quant = fmt
+        return self
+
+    def _use_w8_decode(self) -> bool:
+        return (getattr(self, "quant", None) is not None
+                and not getattr(self, "no_w8_decode", False))
+
     def _can_fuse_decode(self, T: int) -> bool:
         import os
         if os.environ.get("AF_NO_FUSED_DECODE") == "1":
@@ -407,9 +472,11 @@ class LlamaForCausalLM(nn.Module):
             ss = torch.empty(T, 8, dtype=torch.float32, device=ids.device)
             ss2 = torch.empty_like(ss)
             residual = ops.embedding(ids, self.embed, ss=ss)
+            w8 = self._use_w8_decode()
             for layer in self.layers:
                 residual, ss = layer.forward_decode_fused(
-                    residual, ss, ss2, positions, self.rope_tab, kv, md)
+                    residual, ss, ss2, positions, self.rope_tab, kv, md,
+                    w8=w8, w8_min_elems=self.w8_min_elems)
             h = ops.rmsnorm(residual, self.final_norm, self.cfg.rms_eps)
             return self._project_logits(h)
         h = ops.embedding(ids, self.embed)

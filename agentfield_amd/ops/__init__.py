@@ -243,11 +243,36 @@ def choose_sk(N: int, K: int) -> int:
     return sk
 
 
+def _check_wq(x: torch.Tensor, w: torch.Tensor, wq) -> None:
+    """Validate the MX-fp8 operands of linear_skinny before any launch."""
+    try:
+        w8, sw = wq
+    except (TypeError, ValueError):
+        raise ValueError("wq must be a (w8, sw) pair of tensors") from None
+    N, K = w.shape
+    if w8.dtype != torch.uint8 or sw.dtype != torch.uint8:
+        raise ValueError(f"wq tensors must be uint8 (e4m3 bytes, E8M0 scales),"
+                         f" got {w8.dtype} and {sw.dtype}")
+    if tuple(w8.shape) != (N, K):
+        raise ValueError(f"w8 shape {tuple(w8.shape)} != w shape {(N, K)}")
+    if K % 32 or tuple(sw.shape) != (N, K // 32):
+        raise ValueError(f"sw shape {tuple(sw.shape)} != {(N, K // 32)} "
+                         "(one scale per 32-element K-block)")
+    if not (w8.is_contiguous() and sw.is_contiguous()):
+        raise ValueError("w8 and sw must be contiguous")
+    if w8.device != x.device or sw.device != x.device:
+        raise ValueError(f"w8/sw on {w8.device}/{sw.device}, x on {x.device}")
+    if w8.data_ptr() % 16 or sw.data_ptr() % 2:
+        raise ValueError("w8 must be 16-byte and sw 2-byte aligned")
+
+
 def linear_skinny(x: torch.Tensor, w: torch.Tensor, mode: int = 0,
                   residual: torch.Tensor | None = None,
                   sk: int | None = None,
                   scale: tuple | None = None,
-                  ss_out: torch.Tensor | None = None) -> torch.Tensor:
+                  ss_out: torch.Tensor | None = None,
+                  wq: tuple[torch.Tensor, torch.Tensor] | None = None
+                  ) -> torch.Tensor:
     """Decode-path GEMM (M<=256) via the MFMA weight-streaming kernel.
 
     mode 0: plain; mode 1: +residual (in-place update); mode 2: fused SwiGLU
@@ -257,9 +282,15 @@ def linear_skinny(x: torch.Tensor, w: torch.Tensor, mode: int = 0,
     the OUTPUT (valid when the norm weight is folded into w — see
     LlamaForCausalLM.fold_norm_weights); x itself stays unnormalized so the
     weight stream keeps its async global_load_lds pipeline.
+    wq=(w8, sw): stream w as MX-fp8 (quant.quantize_mx: e4m3 bytes [N,K] +
+    E8M0 scales [N,K/32]) instead of bf16.  w must hold exactly
+    dequantize_mx(w8, sw); it gives the shape and is not read on the device.
+    The result is bit-identical to the bf16 path on that w.
     """
     M, K = x.shape
     N = w.shape[0]
+    if wq is not None:
+        _check_wq(x, w, wq)
     if sk is None:
         sk = choose_sk(N, K)
     cols = N // 2 if mode == 2 else N
@@ -271,6 +302,13 @@ def linear_skinny(x: torch.Tensor, w: torch.Tensor, mode: int = 0,
     else:
         ss_p = _lib.ptr(None)
         eps = 0.0
+    if wq is not None:
+        rc = _lib.lib().af_gemm_skinny_w8(
+            _lib.ptr(out), _lib.ptr(partial), _lib.ptr(residual), _lib.ptr(x),
+            _lib.ptr(wq[0]), _lib.ptr(wq[1]), M, N, K, sk, mode, ss_p, eps,
+            _lib.ptr(ss_out), _lib.cur_stream())
+        _lib.check(rc, "af_gemm_skinny_w8")
+        return out
     rc = _lib.lib().af_gemm_skinny(
         _lib.ptr(out), _lib.ptr(partial), _lib.ptr(residual), _lib.ptr(x),
         _lib.ptr(w), M, N, K, sk, mode, ss_p, eps, _lib.ptr(ss_out),

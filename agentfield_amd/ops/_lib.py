@@ -63,6 +63,8 @@ def _declare(l: ctypes.CDLL) -> None:
                                        ctypes.c_long, ctypes.c_ulonglong, p]
     l.af_gemm_skinny.argtypes = [p, p, p, p, p, i, i, i, i, i,
                                  p, f, p, p]
+    l.af_gemm_skinny_w8.argtypes = [p, p, p, p, p, p, i, i, i, i, i,
+                                    p, f, p, p]
     l.af_sample.argtypes = [p, p, p, p, p, p, u32, i, i, p]
     l.af_sample_topkp.argtypes = [p, p, p, p, p, p, p, p, p, p, p, p,
                                   u32, i, i, p]
@@ -80,7 +82,7 @@ def _declare(l: ctypes.CDLL) -> None:
     for fn in ("af_rmsnorm", "af_rope_cache", "af_silu_mul", "af_add",
                "af_reshape_and_cache", "af_embedding", "af_attn_decode",
                "af_attn_prefill", "af_gemm_bf16", "af_gemm_bf16_ring", "af_gemm_bf16_q8", "af_gemm_mxfp8", "af_oneshot_allreduce",
-               "af_gemm_skinny", "af_sample",
+               "af_gemm_skinny", "af_gemm_skinny_w8", "af_sample",
                "af_sample_topkp", "af_sample_masked",
                "af_sample_topkp_masked", "af_mask_logits", "af_gather_rows", "af_mfma_probe", "af_mfma_mx_probe", "af_lds_stride_probe", "af_mfma_mx32_probe", "af_axpy",
                "af_device_sync"):

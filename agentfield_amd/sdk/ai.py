@@ -321,6 +321,10 @@ def get_runner(cfg: AIConfig) -> EngineRunner:
         # (opt out with AGENTFIELD_NO_PREFIX_CACHE=1)
         kw["prefix_cache"] = os.environ.get(
             "AGENTFIELD_NO_PREFIX_CACHE") != "1"
+        # opt-in weight quantization (AGENTFIELD_QUANT=mxfp8); unset = bf16
+        quant = os.environ.get("AGENTFIELD_QUANT")
+        if quant:
+            kw["quant"] = quant
         eng = LLMEngine(model_cfg, device=device, **kw)
         runner = EngineRunner(eng, tokenizer)
         _runners[key] = runner

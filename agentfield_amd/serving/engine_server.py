@@ -101,6 +101,7 @@ def create_engine_app(runner: EngineRunner, model_name: str,
             "running": eng.sched.num_running(),
             "kv_free_pages": eng.sched.alloc.num_free,
             "kv_total_pages": eng.sched.alloc.num_pages,
+            "quant": getattr(eng, "quant", None),
             **eng.metrics,
         }
         ct = getattr(eng.sched, "cached_tokens", None)
@@ -520,7 +521,7 @@ def create_engine_app(runner: EngineRunner, model_name: str,
     return app
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", action="append", default=None,
                     help="model to serve (repeatable: the first is the "
@@ -545,7 +546,15 @@ def main():
     ap.add_argument("--prefix-cache", action="store_true",
                     help="share paged KV across requests with a common "
                          "prompt prefix (refcounted pages, LRU eviction)")
-    args = ap.parse_args()
+    ap.add_argument("--quant", choices=["mxfp8"], default=None,
+                    help="weight quantization for every served model: "
+                         "mxfp8 streams the layer projections as e4m3 + "
+                         "E8M0 block scales at decode (docs/QUANTIZATION.md)")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
 
     device = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
     if device.startswith("cuda:"):
@@ -568,7 +577,7 @@ def main():
             enable_graphs=not args.no_graphs and device.startswith("cuda"),
             spec_lookup=args.spec_lookup,
             spec_draft=args.spec_draft, spec_draft_k=args.spec_draft_k,
-            prefix_cache=args.prefix_cache, **kw)
+            prefix_cache=args.prefix_cache, quant=args.quant, **kw)
         return EngineRunner(eng, tokenizer)
 
     runners = {name: build(name) for name in models}

@@ -85,6 +85,78 @@ def bench_skinny():
                           "hipblaslt_tbps": round(gb / t_blas / 1e3, 2),
                           "ours_us": round(t_ours * 1e6, 1),
                           "blas_us": round(t_blas * 1e6, 1)}))
+    bench_skinny_w8()
+
+
+LLC_BYTES = 256 << 20   # MI355X Infinity Cache
+
+
+def _rotation_us(fns, reps=7):
+    """Median / min / max microseconds per call over `reps` passes through
+    every callable of `fns` (one per distinct weight buffer)."""
+    ts = []
+    for _ in range(reps):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for fn in fns:
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        ts.append(t0.elapsed_time(t1) * 1e3 / len(fns))
+    ts.sort()
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def bench_skinny_w8(ms=(16, 64, 128)):
+    """bf16 vs MX-fp8 weight stream on the decode projections, same process,
+    alternating.  Each path walks a rotation of distinct weight buffers
+    larger than twice the last-level cache: a decode step never finds a
+    layer's weights cached, a single reused matrix would be."""
+    shapes = {"qkv": (6144, 4096), "o": (4096, 4096),
+              "gate_up": (28672, 4096), "down": (4096, 14336)}
+    for M in ms:
+        for name, (N, K) in shapes.items():
+            a = torch.randn(M, K, dtype=torch.bfloat16, device=DEV)
+            b16, b8 = N * K * 2, N * K + N * K // 32
+            n16 = 2 * LLC_BYTES // b16 + 2
+            n8 = 2 * LLC_BYTES // b8 + 2
+            w16 = [torch.randn(N, K, dtype=torch.bfloat16, device=DEV)
+                   for _ in range(n16)]
+            w8s = []
+            for _ in range(n8):
+                q = torch.randint(0, 256, (N, K), dtype=torch.uint8,
+                                  device=DEV)
+                q[(q & 0x7f) == 0x7f] = 0   # no NaN codes
+                w8s.append((q, torch.randint(118, 124, (N, K // 32),
+                                             dtype=torch.uint8, device=DEV)))
+            f16 = [lambda w=w: ops.linear_skinny(a, w) for w in w16]
+            f8 = [lambda wq=wq: ops.linear_skinny(a, w16[0], wq=wq)
+                  for wq in w8s]
+            _rotation_us(f16, reps=1), _rotation_us(f8, reps=1)   # warm up
+            r16, r8 = [], []
+            for _ in range(3):   # alternate the two paths
+                r16.append(_rotation_us(f16))
+                r8.append(_rotation_us(f8))
+            m16 = sorted(r[0] for r in r16)[1]
+            m8 = sorted(r[0] for r in r8)[1]
+            lo16, hi16 = min(r[1] for r in r16), max(r[2] for r in r16)
+            lo8, hi8 = min(r[1] for r in r8), max(r[2] for r in r8)
+            row = {"op": "gemm_skinny_w8", "proj": name, "MNK": [M, N, K],
+                   "bf16_us": round(m16, 1), "w8_us": round(m8, 1),
+                   "bf16_tbps": round(b16 / m16 / 1e6, 2),
+                   "w8_tbps": round(b8 / m8 / 1e6, 2),
+                   "w8_over_bf16": round(m8 / m16, 3),
+                   "bf16_spread_us": [round(lo16, 1), round(hi16, 1)],
+                   "w8_spread_us": [round(lo8, 1), round(hi8, 1)],
+                   "buffers": [n16, n8]}
+            if M == 128 and name in ("qkv", "gate_up"):
+                blas = [lambda w=w: a @ w.t() for w in w16]
+                _rotation_us(blas, reps=1)
+                row["blas_us"] = round(_rotation_us(blas)[0], 1)
+            print(json.dumps(row), flush=True)
+            del w16, w8s, f16, f8
+            torch.cuda.empty_cache()
 
 
 def bench_prefill(Hq=32, Hk=8, D=128, page=16):
