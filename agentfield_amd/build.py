@@ -35,6 +35,7 @@ HIP_SOURCES = [
     "allreduce.hip",
     "gemm_skinny.hip",
     "gemm_skinny_w8.hip",
+    "gemm_skinny_w4.hip",
     "sampling.hip",
     "probe.hip",
 ]

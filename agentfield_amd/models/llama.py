@@ -296,7 +296,8 @@ class LlamaLayer(nn.Module):
         return h, residual
 
     def forward_decode_fused(self, residual, ss, ss2, positions, rope_tab,
-                             kv, md, w8: bool = False, w8_min_elems: int = 0):
+                             kv, md, w8: bool = False, w8_min_elems: int = 0,
+                             w4: bool = False, w4_min_elems: int = 0):
         """Decode fast path: RMSNorms fold into the skinny GEMMs — input
         normalization happens in the GEMM's X staging (from per-row
         sum-of-squares stats), residual-add + next-norm stats in the GEMM
@@ -306,21 +307,31 @@ class LlamaLayer(nn.Module):
         quantize_weights registered (same matrix, half the bytes, same
         bits out).  At M <= 64 a matrix of fewer than w8_min_elems elements
         keeps its bf16 stream: there the fp8 stream measured no faster
-        (docs/QUANTIZATION.md)."""
+        (docs/QUANTIZATION.md).
+
+        w4 / w4_min_elems: the same for the MX-fp4 buffers (_q4 / _s4) of
+        quant="mxfp4", except that the size cut-off holds at every M: above
+        64 rows the fp4 stream measured faster on down only, not on o.  A
+        model holds one format, so at most one of w8 and w4 is set."""
         at, mlp = self.attn, self.mlp
         M = residual.shape[0]
 
         def wq(mod, name):
-            if not w8 or (M <= 64
-                          and getattr(mod, name).numel() < w8_min_elems):
-                return None
-            return getattr(mod, name + "_q8"), getattr(mod, name + "_s8")
+            """linear_skinny's weight-stream keywords for this projection."""
+            numel = getattr(mod, name).numel()
+            if w8 and not (M <= 64 and numel < w8_min_elems):
+                return {"wq": (getattr(mod, name + "_q8"),
+                               getattr(mod, name + "_s8"))}
+            if w4 and numel >= w4_min_elems:
+                return {"wq4": (getattr(mod, name + "_q4"),
+                                getattr(mod, name + "_s4"))}
+            return {}
         M = residual.shape[0]
         K = residual.shape[1]
         small = M <= 64  # measured crossover vs hipBLASLt (BENCHMARKS.md)
         if small:
             qkv = ops.linear_skinny(residual, at.qkv, scale=(ss, self.eps),
-                                    wq=wq(at, "qkv"))
+                                    **wq(at, "qkv"))
             o = at.attend(qkv, positions, rope_tab, kv, md)
         else:
             # blas GEMM on the un-normalized rows; the RMSNorm scalar rides
@@ -329,16 +340,16 @@ class LlamaLayer(nn.Module):
             o = at.attend(qkv, positions, rope_tab, kv, md,
                           scale=(ss, K, self.eps))
         ops.linear_skinny(o, at.o, mode=4, residual=residual, ss_out=ss2,
-                          wq=wq(at, "o"))
+                          **wq(at, "o"))
         if small:
             act = ops.linear_skinny(residual, mlp.gate_up, mode=2,
                                     scale=(ss2, self.eps),
-                                    wq=wq(mlp, "gate_up"))
+                                    **wq(mlp, "gate_up"))
         else:
             act = ops.silu_and_mul(residual @ mlp.gate_up.t(),
                                    scale=(ss2, K, self.eps))
         ops.linear_skinny(act, mlp.down, mode=4, residual=residual, ss_out=ss,
-                          wq=wq(mlp, "down"))
+                          **wq(mlp, "down"))
         return residual, ss
 
 
@@ -352,6 +363,13 @@ class LlamaForCausalLM(nn.Module):
     # dominated by fixed costs, not bytes.  0 sends every projection through
     # the fp8 kernel.
     w8_min_elems = 1 << 25
+    # quant="mxfp4" decode dispatch: at every M only matrices of at least
+    # this many elements stream as fp4.  Measured on MI355X (same shapes,
+    # docs/QUANTIZATION.md, fp4 table): gate_up and down are faster as fp4
+    # wherever the skinny kernel serves them (M = 16, 64; down also at 128);
+    # o never is, qkv only at M = 16.  0 sends every projection through the
+    # fp4 kernel.
+    w4_min_elems = 1 << 25
 
     def __init__(self, cfg: LlamaConfig, device="cpu", dtype=torch.bfloat16):
         super().__init__()
@@ -413,7 +431,9 @@ class LlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def quantize_weights(self, fmt: str = "mxfp8"):
         """Put every dense layer's qkv / o / gate_up / down on the MX-fp8
-        grid (OCP e4m3 + one E8M0 scale per 32-element K-block).
+        grid (OCP e4m3 + one E8M0 scale per 32-element K-block) or, with
+        fmt="mxfp4", on the MX-fp4 grid (OCP e2m1, same scales; buffers
+        <name>_q4 [N, K/2] / <name>_s4, about 1.28x the bf16 bytes resident).
 
         The bf16 parameter is overwritten with the dequantized values —
         exactly representable, so every path that reads the parameter
@@ -424,24 +444,32 @@ class LlamaForCausalLM(nn.Module):
         (about 1.53x the bf16 bytes of these matrices).  embed, lm_head,
         norms and the router are left alone.  Run after fold_norm_weights:
         folding rewrites qkv and gate_up."""
-        from ..quant import dequantize_mx, quantize_mx
-        if fmt != "mxfp8":
+        from ..quant import (dequantize_mx, dequantize_mx4, quantize_mx,
+                             quantize_mx4)
+        if fmt not in ("mxfp8", "mxfp4"):
             raise ValueError(f"unknown quantization format {fmt!r} "
-                             "(supported: 'mxfp8')")
+                             "(supported: 'mxfp8', 'mxfp4')")
         if self.cfg.num_experts > 1:
             raise ValueError("quantize_weights: MoE expert weights are not "
                              "supported yet")
-        if getattr(self, "quant", None) == fmt:
+        have = getattr(self, "quant", None)
+        if have == fmt:
             return self
+        if have is not None:
+            raise ValueError(f"model is already quantized as {have!r}; "
+                             f"cannot requantize as {fmt!r}")
+        quantize, dequantize, sfx = (
+            (quantize_mx, dequantize_mx, "8") if fmt == "mxfp8"
+            else (quantize_mx4, dequantize_mx4, "4"))
         for layer in self.layers:
             for mod, name in ((layer.attn, "qkv"), (layer.attn, "o"),
                               (layer.mlp, "gate_up"), (layer.mlp, "down")):
                 w = getattr(mod, name)
-                q8, s8 = quantize_mx(w)
-                w.copy_(dequantize_mx(q8, s8).to(w.dtype))
-                mod.register_buffer(name + "_q8", q8.contiguous(),
+                q, sc = quantize(w)
+                w.copy_(dequantize(q, sc).to(w.dtype))
+                mod.register_buffer(name + "_q" + sfx, q.contiguous(),
                                     persistent=False)
-                mod.register_buffer(name + "_s8", s8.contiguous(),
+                mod.register_buffer(name + "_s" + sfx, sc.contiguous(),
                                     persistent=False)
         self.quant = fmt
         return self
@@ -472,11 +500,14 @@ class LlamaForCausalLM(nn.Module):
             ss = torch.empty(T, 8, dtype=torch.float32, device=ids.device)
             ss2 = torch.empty_like(ss)
             residual = ops.embedding(ids, self.embed, ss=ss)
-            w8 = self._use_w8_decode()
+            stream = self._use_w8_decode()
+            w8 = stream and self.quant == "mxfp8"
+            w4 = stream and self.quant == "mxfp4"
             for layer in self.layers:
                 residual, ss = layer.forward_decode_fused(
                     residual, ss, ss2, positions, self.rope_tab, kv, md,
-                    w8=w8, w8_min_elems=self.w8_min_elems)
+                    w8=w8, w8_min_elems=self.w8_min_elems,
+                    w4=w4, w4_min_elems=self.w4_min_elems)
             h = ops.rmsnorm(residual, self.final_norm, self.cfg.rms_eps)
             return self._project_logits(h)
         h = ops.embedding(ids, self.embed)

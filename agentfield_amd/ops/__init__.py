@@ -266,12 +266,37 @@ def _check_wq(x: torch.Tensor, w: torch.Tensor, wq) -> None:
         raise ValueError("w8 must be 16-byte and sw 2-byte aligned")
 
 
+def _check_wq4(x: torch.Tensor, w: torch.Tensor, wq4) -> None:
+    """Validate the MX-fp4 operands of linear_skinny before any launch."""
+    try:
+        w4, sw = wq4
+    except (TypeError, ValueError):
+        raise ValueError("wq4 must be a (w4, sw) pair of tensors") from None
+    N, K = w.shape
+    if w4.dtype != torch.uint8 or sw.dtype != torch.uint8:
+        raise ValueError(f"wq4 tensors must be uint8 (packed e2m1 codes, E8M0"
+                         f" scales), got {w4.dtype} and {sw.dtype}")
+    if K % 32 or tuple(w4.shape) != (N, K // 2):
+        raise ValueError(f"w4 shape {tuple(w4.shape)} != {(N, K // 2)} "
+                         "(two codes per byte)")
+    if tuple(sw.shape) != (N, K // 32):
+        raise ValueError(f"sw shape {tuple(sw.shape)} != {(N, K // 32)} "
+                         "(one scale per 32-element K-block)")
+    if not (w4.is_contiguous() and sw.is_contiguous()):
+        raise ValueError("w4 and sw must be contiguous")
+    if w4.device != x.device or sw.device != x.device:
+        raise ValueError(f"w4/sw on {w4.device}/{sw.device}, x on {x.device}")
+    if w4.data_ptr() % 16 or sw.data_ptr() % 2:
+        raise ValueError("w4 must be 16-byte and sw 2-byte aligned")
+
+
 def linear_skinny(x: torch.Tensor, w: torch.Tensor, mode: int = 0,
                   residual: torch.Tensor | None = None,
                   sk: int | None = None,
                   scale: tuple | None = None,
                   ss_out: torch.Tensor | None = None,
-                  wq: tuple[torch.Tensor, torch.Tensor] | None = None
+                  wq: tuple[torch.Tensor, torch.Tensor] | None = None,
+                  wq4: tuple[torch.Tensor, torch.Tensor] | None = None
                   ) -> torch.Tensor:
     """Decode-path GEMM (M<=256) via the MFMA weight-streaming kernel.
 
@@ -286,11 +311,19 @@ def linear_skinny(x: torch.Tensor, w: torch.Tensor, mode: int = 0,
     E8M0 scales [N,K/32]) instead of bf16.  w must hold exactly
     dequantize_mx(w8, sw); it gives the shape and is not read on the device.
     The result is bit-identical to the bf16 path on that w.
+    wq4=(w4, sw): the same with MX-fp4 (quant.quantize_mx4: e2m1 codes packed
+    two per byte [N,K/2], even k in the low nibble, + E8M0 scales [N,K/32]);
+    w must hold exactly dequantize_mx4(w4, sw).  Also bit-identical to the
+    bf16 path on that w.  wq and wq4 are mutually exclusive.
     """
     M, K = x.shape
     N = w.shape[0]
+    if wq is not None and wq4 is not None:
+        raise ValueError("wq and wq4 are mutually exclusive")
     if wq is not None:
         _check_wq(x, w, wq)
+    if wq4 is not None:
+        _check_wq4(x, w, wq4)
     if sk is None:
         sk = choose_sk(N, K)
     cols = N // 2 if mode == 2 else N
@@ -308,6 +341,13 @@ def linear_skinny(x: torch.Tensor, w: torch.Tensor, mode: int = 0,
             _lib.ptr(wq[0]), _lib.ptr(wq[1]), M, N, K, sk, mode, ss_p, eps,
             _lib.ptr(ss_out), _lib.cur_stream())
         _lib.check(rc, "af_gemm_skinny_w8")
+        return out
+    if wq4 is not None:
+        rc = _lib.lib().af_gemm_skinny_w4(
+            _lib.ptr(out), _lib.ptr(partial), _lib.ptr(residual), _lib.ptr(x),
+            _lib.ptr(wq4[0]), _lib.ptr(wq4[1]), M, N, K, sk, mode, ss_p, eps,
+            _lib.ptr(ss_out), _lib.cur_stream())
+        _lib.check(rc, "af_gemm_skinny_w4")
         return out
     rc = _lib.lib().af_gemm_skinny(
         _lib.ptr(out), _lib.ptr(partial), _lib.ptr(residual), _lib.ptr(x),

@@ -546,10 +546,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--prefix-cache", action="store_true",
                     help="share paged KV across requests with a common "
                          "prompt prefix (refcounted pages, LRU eviction)")
-    ap.add_argument("--quant", choices=["mxfp8"], default=None,
+    ap.add_argument("--quant", choices=["mxfp8", "mxfp4"], default=None,
                     help="weight quantization for every served model: "
-                         "mxfp8 streams the layer projections as e4m3 + "
-                         "E8M0 block scales at decode (docs/QUANTIZATION.md)")
+                         "mxfp8 / mxfp4 stream the layer projections as "
+                         "e4m3 / e2m1 + E8M0 block scales at decode "
+                         "(docs/QUANTIZATION.md)")
     return ap
 
 

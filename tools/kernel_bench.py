@@ -159,6 +159,63 @@ def bench_skinny_w8(ms=(16, 64, 128)):
             torch.cuda.empty_cache()
 
 
+def bench_skinny_w4(ms=(16, 64, 128)):
+    """bf16 vs MX-fp8 vs MX-fp4 weight stream on the decode projections:
+    bench_skinny_w8's method (same process, the paths alternating, each over
+    a rotation of distinct weight buffers larger than twice the last-level
+    cache) with a third column."""
+    shapes = {"qkv": (6144, 4096), "o": (4096, 4096),
+              "gate_up": (28672, 4096), "down": (4096, 14336)}
+    for M in ms:
+        for name, (N, K) in shapes.items():
+            a = torch.randn(M, K, dtype=torch.bfloat16, device=DEV)
+            nbytes = {"bf16": N * K * 2, "w8": N * K + N * K // 32,
+                      "w4": N * K // 2 + N * K // 32}
+            count = {p: 2 * LLC_BYTES // b + 2 for p, b in nbytes.items()}
+            w16 = [torch.randn(N, K, dtype=torch.bfloat16, device=DEV)
+                   for _ in range(count["bf16"])]
+
+            def scales():
+                return torch.randint(118, 124, (N, K // 32),
+                                     dtype=torch.uint8, device=DEV)
+            w8s, w4s = [], []
+            for _ in range(count["w8"]):
+                q = torch.randint(0, 256, (N, K), dtype=torch.uint8,
+                                  device=DEV)
+                q[(q & 0x7f) == 0x7f] = 0   # no NaN codes
+                w8s.append((q, scales()))
+            for _ in range(count["w4"]):
+                w4s.append((torch.randint(0, 256, (N, K // 2),
+                                          dtype=torch.uint8, device=DEV),
+                            scales()))
+            fns = {"bf16": [lambda w=w: ops.linear_skinny(a, w) for w in w16],
+                   "w8": [lambda wq=wq: ops.linear_skinny(a, w16[0], wq=wq)
+                          for wq in w8s],
+                   "w4": [lambda wq=wq: ops.linear_skinny(a, w16[0], wq4=wq)
+                          for wq in w4s]}
+            runs = {p: [] for p in fns}
+            for f in fns.values():
+                _rotation_us(f, reps=1)   # warm up
+            for _ in range(3):   # alternate the paths
+                for p, f in fns.items():
+                    runs[p].append(_rotation_us(f))
+            row = {"op": "gemm_skinny_w4", "proj": name, "MNK": [M, N, K],
+                   "buffers": [count[p] for p in fns]}
+            for p, r in runs.items():
+                med = sorted(x[0] for x in r)[1]
+                row[p + "_us"] = round(med, 1)
+                row[p + "_spread_us"] = [round(min(x[1] for x in r), 1),
+                                         round(max(x[2] for x in r), 1)]
+                row[p + "_tbps"] = round(nbytes[p] / med / 1e6, 2)
+            if M == 128 and name in ("qkv", "gate_up"):
+                blas = [lambda w=w: a @ w.t() for w in w16]
+                _rotation_us(blas, reps=1)
+                row["blas_us"] = round(_rotation_us(blas)[0], 1)
+            print(json.dumps(row), flush=True)
+            del w16, w8s, w4s, fns
+            torch.cuda.empty_cache()
+
+
 def bench_prefill(Hq=32, Hk=8, D=128, page=16):
     for (B, S) in [(16, 512), (4, 2048), (1, 8192)]:
         T = B * S
@@ -235,6 +292,7 @@ if __name__ == "__main__":
     args = ap.parse_args()
     torch.manual_seed(0)
     for name, fn in [("gemm", bench_gemm), ("skinny", bench_skinny),
+                     ("skinny_w4", bench_skinny_w4),
                      ("prefill", bench_prefill),
                      ("decode", bench_decode), ("norm", bench_norm_rope),
                      ("sample", bench_sample)]:
